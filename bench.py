@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the kernel-recombination step (BASELINE.json metric) on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config C]
+    python bench.py --gpus N --steps K --warmup W [--config C] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W [--config C]          (N > 1)
 
@@ -157,6 +157,29 @@ def t(a):
     return torch.from_numpy(np.ascontiguousarray(a))
 
 
+DUMP_MAX_ELEMENTS = 2 ** 21          # per array (16 MB as float64); a longer one is dumped as a fixed, seeded sample
+
+
+def dump_outputs(dir_, arrays):
+    """`--dump-outputs DIR`: what the timed path returned in its last timed step, one float64 `DIR/<name>.npy` per array
+    (indices as exact float64).  An array longer than DUMP_MAX_ELEMENTS is written as `<name>_sample.npy`, the elements at
+    `<name>_sample_index.npy` (sorted positions drawn with numpy seed 0: the same positions run to run), so the whole dump
+    stays below 64 MB.  -> {file name: shape} for the JSON line."""
+    os.makedirs(dir_, exist_ok=True)
+    written = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        a = a.astype(np.float64)
+        if a.size > DUMP_MAX_ELEMENTS:
+            pos = np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMENTS, replace=False))
+            np.save(os.path.join(dir_, f"{name}_sample_index.npy"), pos.astype(np.float64))
+            written[f"{name}_sample_index.npy"] = list(pos.shape)
+            a, name = a.reshape(-1)[pos], f"{name}_sample"
+        np.save(os.path.join(dir_, f"{name}.npy"), a)
+        written[f"{name}.npy"] = list(a.shape)
+    return written
+
+
 def build_inputs(cfg, rank, world, dev):
     """-> (X_cand, X_nys, mu0 on the device, spec, host inputs or None, rows on this rank)."""
     case = {k: v for k, v in cfg.items() if k not in ("name", "golden", "strong", "cpu_sample_N", "device_pool")}
@@ -299,6 +322,9 @@ def funnel(args):
         w_b, X_b = next_batch(sob)
     torch.cuda.synchronize()
     ms_per_step = (time.perf_counter() - t0) / args.steps * 1e3
+    dumped = None
+    if args.funnel and args.dump_outputs:                             # (the headline line only, not the sub-record)
+        dumped = dump_outputs(args.dump_outputs, {"w_batch": w_b, "X_batch": X_b})
     # per phase: the four calls bracketed by synchronisations
     phases = {"pi_weights": 0.0, "cleansing_weights": 0.0, "kmeans_resampling": 0.0, "sampling_recombination": 0.0}
     calls = {k: 0 for k in phases}
@@ -415,6 +441,8 @@ def funnel(args):
         "ms_per_step_with_phase_brackets": ms_bracketed,
         "cpu_baseline": cpu, "parity": parity, "n_selected": int(X_b.shape[0]),
     }
+    if dumped is not None:
+        out["dumped_outputs"] = {"dir": args.dump_outputs, "files": dumped}
     return out
 
 
@@ -442,7 +470,13 @@ def main():
                     help="default line (one GPU, configuration 2): skip the `other_configs` (BASELINE.json configurations 1, 3, 4, 5, "
                          "--other-steps steps each, no CPU leg) and `acquisition_step` (Sober.next_batch) sub-records")
     ap.add_argument("--other-steps", type=int, default=10)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last timed step to DIR/<name>.npy (float64): the "
+                         "selected indices, their weights and the init_weights the call updated in place (--funnel: the "
+                         "batch and its weights); rank 0's shard for N > 1")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.funnel:
         print(json.dumps(funnel(args)))
         return
@@ -602,6 +636,9 @@ def measure(args, config, rank, world, dev, group, backend):
     torch.cuda.synchronize(); barrier()
     elapsed = time.perf_counter() - t0
     gc.enable()
+    dumped = None
+    if rank == 0 and args.dump_outputs and not light and not args.funnel:   # (the headline line only, not the sub-records)
+        dumped = dump_outputs(args.dump_outputs, {"idx": idx, "w": w, "init_weights_after": mu})
     if world > 1:
         import torch.distributed as dist
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
@@ -830,6 +867,8 @@ def measure(args, config, rank, world, dev, group, backend):
         "ms_per_step_median": round(sorted(per_step)[len(per_step) // 2] * 1e3, 3),    # (the steps without event pairs or host hiccups)
         "n_selected": int(idx.numel()),
     }
+    if dumped is not None:
+        out["dumped_outputs"] = {"dir": args.dump_outputs, "files": dumped}
     gc.enable()
     return out
 

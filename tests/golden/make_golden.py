@@ -31,7 +31,7 @@ sys.path.insert(0, ROOT)
 REF = "/root/reference/SOBER"
 
 from oracle import sober_oracle as O  # noqa: E402
-from tests.golden.synth import synth, build_spec, checksum, calc_obj_fn, SEED_CALL  # noqa: E402
+from tests.golden.synth import synth, build_spec, checksum, calc_obj_fn, load_case, SEED_CALL  # noqa: E402
 
 
 # --------------------------------------------------------------------------- #
@@ -667,12 +667,200 @@ def gen_kmeans_screened(ref):
     np.savez_compressed(os.path.join(HERE, "kmeans_screened.npz"), **out)
 
 
+def fuzz_cases():
+    """The 64 seeded random recombination cases of tests/test_oracle_vs_reference_fuzz.py: kinds x modes x leftovers of
+    every kind x calc_obj x zero weights x ARD (inputs from synth(case), so only the cases' parameters are code)."""
+    rng = np.random.default_rng(20261003)
+    kinds = [O.RBF, O.MATERN52, O.TANIMOTO]
+    modes = ["predictive_covariance", "weighted_predictive_covariance", "kernel"]
+    out = []
+    for i in range(64):
+        kind = kinds[i % 3] if i % 8 != 7 else O.TANIMOTO
+        mode = modes[(i // 3) % 3]
+        b = int(rng.integers(4, 25))
+        # leftovers of every kind: R mod 2b in {0, 1, 2b-1, random}, pools below one level (straight to the final level),
+        # pools of exactly one level
+        shape = i % 6
+        S = 2 * b
+        E = int(rng.integers(2, 30))
+        N = {0: E * S, 1: E * S + 1, 2: E * S + S - 1, 3: E * S + int(rng.integers(1, S)),
+             4: int(rng.integers(b + 1, S + 1)), 5: S + int(rng.integers(1, S))}[shape]
+        d = int(rng.integers(2, 9)) if kind != O.TANIMOTO else int(rng.choice([64, 96, 128, 200]))
+        M = int(rng.integers(max(b + 2, 20), 90))
+        M = min(M, N)
+        case = dict(name=f"fuzz{i}", kind=kind, mode=mode, N=N, M=M, d=d, b=b, n_obs=int(rng.integers(5, 40)),
+                    seed=1000 + i, ard=bool(rng.integers(0, 2)) and kind != O.TANIMOTO,
+                    zero_frac=0.25 if i % 5 == 0 else 0.0, calc_obj=(i % 4 == 1),
+                    outputscale=float(rng.uniform(0.5, 2.0)), mean_const=float(rng.uniform(0.2, 1.0)),
+                    bit_p=float(rng.uniform(0.05, 0.3)))
+        if M < b + 1:
+            continue
+        out.append(case)
+    return out
+
+
+def gen_reference_fuzz(ref):
+    """The reference's recombination (run_reference, one thread) on every case of fuzz_cases(): indices, weights and the
+    mutated init_weights, or the reference's own exception where it cannot run the input.  The inputs' checksums are
+    stored beside them, so that a change of synth() shows up as such and not as a parity failure."""
+    out = {}
+    for case in fuzz_cases():
+        n = case["name"]
+        inp = synth(case)
+        out[f"{n}_cks_x"] = checksum(inp["X_cand"])
+        try:
+            rec = run_reference(ref, case, inp, threads=1)
+        except Exception as e:                       # noqa: BLE001  (e.g. a singular step)
+            out[f"{n}_raised"] = np.array(f"{type(e).__name__}: {e}")
+            print(n, "reference raised", type(e).__name__)
+            continue
+        out[f"{n}_idx"], out[f"{n}_w"], out[f"{n}_mu_after"] = rec["idx"].numpy(), rec["w"].numpy(), rec["mu_after"].numpy()
+        print(n, case["kind"], case["mode"], "N", case["N"], "b", case["b"], "->", len(rec["idx"]))
+    np.savez_compressed(os.path.join(HERE, "reference_fuzz.npz"), **out)
+
+
+DROPIN_SAMPLER_CASES = ("cfg1_rbf_ard", "rbf_b30", "matern_b20", "tanimoto_weighted", "rbf_zero_weights")
+
+
+def _record_call(store, tag, args, kwargs):
+    """One call of the reference into `recombination`: how it is made (which arguments positional, which by keyword,
+    device and dtype) and its tensors; the CPU generator's state in front of it (the svd_lowrank draw)."""
+    store[f"{tag}_n_args"] = np.array(len(args))
+    store[f"{tag}_kwargs"] = np.array(sorted(kwargs))
+    X_cand, X_nys, b, _kernel, device, dtype = args
+    store[f"{tag}_X_cand"], store[f"{tag}_X_nys"] = X_cand.numpy().copy(), X_nys.numpy().copy()
+    store[f"{tag}_b"] = np.array(b)
+    store[f"{tag}_device"], store[f"{tag}_dtype"] = np.array(str(device)), np.array(str(dtype))
+    store[f"{tag}_init_weights"] = kwargs["init_weights"].numpy().copy()
+    store[f"{tag}_calc_obj_none"] = np.array(kwargs.get("calc_obj") is None)
+    store[f"{tag}_rng_state"] = torch.get_rng_state().numpy().copy()
+
+
+def gen_dropin(ref):
+    """The reference's own callers of the hot path, recorded: `RecombinationSampler.sampling_recombination`
+    (SOBER/_sampler.py:27-59) on the DROPIN_SAMPLER_CASES goldens, and `Sober.next_batch` (SOBER/_sober.py:125-195) in
+    the scenarios of sober_next_batch.npz (dataset prior with / without pruning and with / without return_weights; a
+    sampled prior).  For every call into `recombination`: the call as made, the generator state in front of it, its
+    result and the mutated init_weights; for every `Kernel(...)` the reference's `Sober` builds: positional count and
+    keywords; for `Sober.next_batch`: its return values and, with pruning, the kept candidates' pool indices.  And the
+    reference's `Sober.should_reset_prior` verdicts on the seeded observation histories of
+    tests/test_dropin_reference.py::test_should_reset_prior_equals_the_reference."""
+    load_sampler_sober(ref)
+    out = {}
+    calls = []
+    orig_rec, orig_kernel = ref["_sampler"].recombination, ref["_sober"].Kernel
+
+    def rec_wrap(*args, **kwargs):
+        tag = f"call{len(calls)}"
+        _record_call(out, tag, args, kwargs)
+        idx, w = orig_rec(*args, **kwargs)
+        out[f"{tag}_idx"], out[f"{tag}_w"] = idx.numpy().copy(), w.numpy().copy()
+        out[f"{tag}_mu_after"] = kwargs["init_weights"].numpy().copy()
+        calls.append(tag)
+        return idx, w
+
+    kernel_call = {}
+
+    def kernel_wrap(*args, **kwargs):
+        kernel_call.update(n_args=np.array(len(args)), kwargs=np.array(sorted(kwargs)),
+                           mode=np.array(kwargs.get("mode", args[1] if len(args) > 1 else "")))
+        return orig_kernel(*args, **kwargs)
+
+    def keep_kernel_call(tag):
+        for k, v in kernel_call.items():
+            out[f"{tag}_kernel_{k}"] = v
+        kernel_call.clear()
+
+    ref["_sampler"].recombination, ref["_sober"].Kernel = rec_wrap, kernel_wrap
+    try:
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            for name in DROPIN_SAMPLER_CASES:
+                case, inp, spec, z = load_case(os.path.join(HERE, f"recomb_{name}.npz"))
+                sampler = ref["_sampler"].RecombinationSampler(ref["_kernel"].Kernel(DuckModel(spec), mode=case["mode"]))
+                torch.manual_seed(SEED_CALL)
+                sampler.sampling_recombination(torch.from_numpy(inp["X_cand"].copy()), torch.from_numpy(inp["X_nys"].copy()),
+                                               torch.from_numpy(inp["mu0"].copy()), case["b"])
+                out[f"sampler_{name}_call"] = np.array(calls[-1])
+                assert np.array_equal(out[f"{calls[-1]}_idx"], z["idx"]), name
+                print("sampler", name, calls[-1])
+            c = SOBER_CASES["dataset"]
+            rng = np.random.default_rng(c["pool_seed"])
+            pool = torch.from_numpy((rng.random((c["pool_n"], c["d"])) < c["pool_p"]).astype(np.float64))
+            model, _ = sober_model(c)
+            for pruning in (True, False):
+                for rw in (False, True):
+                    tag = f"dataset_p{int(pruning)}_w{int(rw)}"
+                    sober = ref["_sober"].Sober(DatasetPrior(pool), model, kernel_type=c["kernel_type"],
+                                                dataset_pruning=pruning)
+                    keep_kernel_call(tag)
+                    orig_sd = sober.sampling_datasets
+
+                    def sd_wrap(n_rec, n_nys, _orig=orig_sd, _tag=tag):
+                        em = _orig(n_rec, n_nys)
+                        if len(em) == 4:
+                            out[f"{_tag}_idx_sampled"] = em[0].numpy().copy()
+                        return em
+                    sober.sampling_datasets = sd_wrap
+                    torch.manual_seed(c["seed_call"])
+                    a, Xb = sober.next_batch(c["n_rec"], c["n_nys"], c["batch"], return_weights=rw)
+                    out[f"{tag}_call"], out[f"{tag}_first"], out[f"{tag}_X"] = np.array(calls[-1]), a.numpy(), Xb.numpy()
+                    print(tag, calls[-1], a.shape, Xb.shape)
+            c = SOBER_CASES["continuous"]
+            model, _ = sober_model(c)
+            sober = ref["_sober"].Sober(UniformPrior(c["d"]), model, kernel_type=c["kernel_type"])
+            keep_kernel_call("continuous")
+            torch.manual_seed(c["seed_call"])
+            Xb = sober.next_batch(c["n_rec"], c["n_nys"], c["batch"])
+            out["continuous_call"], out["continuous_X"] = np.array(calls[-1]), Xb.numpy()
+            print("continuous", calls[-1], Xb.shape)
+    finally:
+        ref["_sampler"].recombination, ref["_sober"].Kernel = orig_rec, orig_kernel
+    out["reset_verdicts"] = np.array(reset_verdicts(ref["_sober"].Sober))
+    print("should_reset_prior", int(out["reset_verdicts"].sum()), "of", out["reset_verdicts"].size)
+    np.savez_compressed(os.path.join(HERE, "dropin_calls.npz"), **out)
+
+
+def reset_histories():
+    """Seeded observation histories for `should_reset_prior` (SOBER/_sober.py:84-123): (n_init, batch_size, y) x 300,
+    each asked with recycle_prior True and False."""
+    rng = np.random.default_rng(5)
+    out = []
+    for _ in range(300):
+        n_init = int(rng.integers(1, 12))
+        bs = int(rng.integers(1, 9))
+        n_batches = int(rng.integers(0, 7))
+        extra = int(rng.integers(0, bs)) if n_batches and rng.random() < 0.3 else 0
+        y = torch.from_numpy(rng.standard_normal(n_init + n_batches * bs + extra))
+        if rng.random() < 0.3:                                           # a maximum early in the history
+            y[int(rng.integers(0, n_init))] = 10.0
+        out.append((n_init, bs, y))
+    return out
+
+
+def reset_verdicts(SoberCls):
+    """`should_reset_prior` of the reference's `Sober` on reset_histories(): a (300, 2) bool array, recycle True / False."""
+    res = []
+    for n_init, bs, y in reset_histories():
+        model = types.SimpleNamespace(train_targets=y)
+        row = []
+        for recycle in (True, False):
+            a = object.__new__(SoberCls)
+            a.fbgp, a.is_bq, a.n_init, a.n_batches_until_reset = False, False, n_init, 3
+            a.pi = types.SimpleNamespace(model=model)
+            a.tensor = torch.tensor
+            row.append(bool(a.should_reset_prior(bs, recycle)))
+        res.append(row)
+    return res
+
+
 if __name__ == "__main__":
-    # python make_golden.py [recombination kmeans kmeans_screened weights psd tanimoto kernel_calls pi wkde basq pruning sober]   (default: all)
+    # python make_golden.py [recombination kmeans kmeans_screened weights psd tanimoto kernel_calls pi wkde basq pruning sober d1 reference_fuzz dropin]   (default: all)
     ref = load_reference()
     gens = {"recombination": gen_recombination, "kmeans": gen_kmeans, "kmeans_screened": gen_kmeans_screened, "weights": gen_weights, "psd": gen_psd,
             "tanimoto": lambda ref: gen_tanimoto(), "kernel_calls": gen_kernel_calls, "pi": gen_pi,
-            "wkde": gen_wkde, "basq": gen_basq, "pruning": gen_pruning, "sober": gen_sober, "d1": gen_d1_sensitivity}
+            "wkde": gen_wkde, "basq": gen_basq, "pruning": gen_pruning, "sober": gen_sober, "d1": gen_d1_sensitivity,
+            "reference_fuzz": gen_reference_fuzz, "dropin": gen_dropin}
     for name in (sys.argv[1:] or list(gens)):
         gens[name](ref)
     tot = sum(os.path.getsize(os.path.join(HERE, f)) for f in os.listdir(HERE) if f.endswith(".npz"))

@@ -1,13 +1,15 @@
-"""Drop-in proof against the reference's OWN callers (build container only: needs /root/reference; skipped on the
-GPU box, where tests/test_hip_parity.py::test_sober_next_batch_vs_reference replays the same calls against fixtures).
+"""Drop-in proof against the reference's OWN callers, replayed from a recording (tests/golden/dropin_calls.npz, written
+by tests/golden/make_golden.py:gen_dropin from the reference's code; tests/test_hip_parity.py::
+test_sober_next_batch_vs_reference replays the same scenarios through the product's `Sober` on the device).
 
-The reference's `RecombinationSampler` (SOBER/_sampler.py:11-59) and `Sober` (SOBER/_sober.py:9-195) are loaded from
-their own files and run UNCHANGED, with the three names of the hot path swapped for this package's:
-`SOBER._sampler.recombination -> sober_amd.recombination`, `SOBER._sober.Kernel -> sober_amd.Kernel` (and with them
-`RecombinationEngine`, the host logic of the product).  Without a GPU the bulk kernels behind `recombination` are the
-CPU test double (tests/_oracle_ops.py); everything else is the code that ships.  Checked: the reference's callers
-get the reference's results (goldens / an unpatched run) through the swapped functions, for `sampling_recombination`
-and for the three return shapes of `Sober.next_batch`."""
+The reference's `RecombinationSampler` (SOBER/_sampler.py:11-59) and `Sober` (SOBER/_sober.py:9-195) reach the hot path
+through two names: `recombination(X_cand, X_nys, batch_size, kernel, device, dtype, init_weights=..., calc_obj=...)`
+and `Kernel(model, mode=...)`.  The recording holds every such call they made -- which arguments positional, which by
+keyword, the tensors, the CPU generator's state in front of it -- with what the reference returned.  Here each call is
+made again, the same way, to `sober_amd.recombination` with a `sober_amd.Kernel` (and with them `RecombinationEngine`,
+the host logic of the product); without a GPU the bulk kernels behind `recombination` are the CPU test double
+(tests/_oracle_ops.py).  Checked: the reference's callers get the reference's results through the swapped functions,
+for `sampling_recombination` and for the three return shapes of `Sober.next_batch`."""
 import os
 import warnings
 
@@ -15,12 +17,10 @@ import numpy as np
 import pytest
 import torch
 
-REF = "/root/reference/SOBER"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="the reference checkout lives in the build container only")
-
-import sober_amd                                                        # noqa: E402
-from tests._oracle_ops import OracleOps                                 # noqa: E402
-from tests.golden.synth import SEED_CALL, build_spec, load_case, synth  # noqa: E402
+import sober_amd
+from tests._oracle_ops import OracleOps
+from tests.golden import make_golden as MG
+from tests.golden.synth import build_spec, load_case, synth
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 
@@ -31,10 +31,7 @@ def _t(a):
 
 @pytest.fixture(scope="module")
 def ref():
-    from tests.golden import make_golden as MG
-    mods = MG.load_sampler_sober(MG.load_reference())
-    mods["MG"] = MG
-    return mods
+    return np.load(os.path.join(GOLD, "dropin_calls.npz"))
 
 
 def _ours(*a, **k):
@@ -43,95 +40,83 @@ def _ours(*a, **k):
         return sober_amd.recombination(*a, **k, _ops=OracleOps())
 
 
-class _Swap:
-    """The three names of the hot path, swapped inside the reference's modules."""
-
-    def __init__(self, ref):
-        self.ref = ref
-
-    def __enter__(self):
-        r = self.ref
-        self.old = (r["_sampler"].recombination, r["_sober"].Kernel)
-        r["_sampler"].recombination = _ours
-        r["_sober"].Kernel = sober_amd.Kernel
-        return self
-
-    def __exit__(self, *exc):
-        self.ref["_sampler"].recombination, self.ref["_sober"].Kernel = self.old
+def _replay(ref, tag, kernel):
+    """The recorded call `tag` made again to sober_amd.recombination, as the reference's caller made it (same positional
+    / keyword split, same generator state) -> (idx, w, init_weights after the call)."""
+    assert int(ref[f"{tag}_n_args"]) == 6
+    assert list(ref[f"{tag}_kwargs"]) == ["calc_obj", "init_weights"] and bool(ref[f"{tag}_calc_obj_none"])
+    assert str(ref[f"{tag}_dtype"]) == "torch.float64"
+    mu = _t(ref[f"{tag}_init_weights"].copy())
+    args = (_t(ref[f"{tag}_X_cand"]), _t(ref[f"{tag}_X_nys"]), int(ref[f"{tag}_b"]), kernel,
+            torch.device(str(ref[f"{tag}_device"])), torch.double)
+    torch.set_rng_state(_t(ref[f"{tag}_rng_state"]))
+    idx, w = _ours(*args, init_weights=mu, calc_obj=None)
+    return idx, w, mu
 
 
-@pytest.mark.parametrize("name", ["cfg1_rbf_ard", "rbf_b30", "matern_b20", "tanimoto_weighted", "rbf_zero_weights"])
+@pytest.mark.parametrize("name", list(MG.DROPIN_SAMPLER_CASES))
 def test_reference_sampler_with_swapped_recombination(ref, name):
     """SOBER/_sampler.py:27-59 calling sober_amd.recombination with a sober_amd.Kernel: the reference golden."""
     case, inp, spec, z = load_case(os.path.join(GOLD, f"recomb_{name}.npz"))
     ks = sober_amd.KernelSpec(spec.kind, spec.lengthscale, spec.outputscale, spec.X_obs, spec.S_cache, spec.noise,
                               spec.mean_const, spec.alpha)
-    with _Swap(ref):
-        sampler = ref["_sampler"].RecombinationSampler(sober_amd.Kernel(ks, case["mode"]))
-        w0 = _t(inp["mu0"].copy())
-        torch.manual_seed(SEED_CALL)
-        idx, w = sampler.sampling_recombination(_t(inp["X_cand"]), _t(inp["X_nys"]), w0, case["b"])
+    tag = str(ref[f"sampler_{name}_call"])
+    assert np.array_equal(ref[f"{tag}_X_cand"], inp["X_cand"]) and np.array_equal(ref[f"{tag}_init_weights"], inp["mu0"])
+    assert int(ref[f"{tag}_b"]) == case["b"]
+    idx, w, w0 = _replay(ref, tag, sober_amd.Kernel(ks, case["mode"]))
     assert np.array_equal(idx.numpy(), z["idx"])
     np.testing.assert_allclose(w.numpy(), z["w"], rtol=1e-9)
     nz = torch.nonzero(w0).flatten().numpy()
     assert np.array_equal(nz, z["mu_after_idx"])                            # Q3 through the reference's caller
+    assert np.array_equal(nz, np.flatnonzero(ref[f"{tag}_mu_after"]))
 
 
-def _model(ref, kind, d, n_obs, seed):
-    case = dict(kind=kind, N=64, M=8, d=d, n_obs=n_obs, seed=seed, mean_const=0.2)
+def _kernel(ref, case, tag):
+    """sober_amd.Kernel built as the reference's `Sober` builds its Kernel (the recorded call: the model, mode= by
+    keyword) from a model of the recorded scenario."""
     inp = synth(case)
     spec = build_spec(case, inp)
-    model = ref["MG"].DuckModel(spec)
-    model.train_targets = torch.zeros(n_obs, dtype=torch.double)
+    model = MG.DuckModel(spec)
+    model.train_targets = torch.zeros(case["n_obs"], dtype=torch.double)
     # (a gpytorch model is read by its class names, sober_amd/_kernel.py:spec_from_model; the duck model of the
     #  fixtures has none, so it carries the spec itself)
     model.kernel_spec = sober_amd.KernelSpec(spec.kind, spec.lengthscale, spec.outputscale, spec.X_obs, spec.S_cache,
                                              spec.noise, spec.mean_const, spec.alpha)
-    return model
-
-
-def _next_batch(ref, prior, model, swapped, seed, **kw):
-    import contextlib
-    cm = _Swap(ref) if swapped else contextlib.nullcontext()
-    with cm, warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        sober = ref["_sober"].Sober(prior, model, kernel_type=kw.pop("kernel_type", "predictive_covariance"),
-                                    dataset_pruning=kw.pop("dataset_pruning", True))
-        torch.manual_seed(seed)
-        return sober.next_batch(**kw)
+    assert int(ref[f"{tag}_kernel_n_args"]) == 1 and list(ref[f"{tag}_kernel_kwargs"]) == ["mode"]
+    assert str(ref[f"{tag}_kernel_mode"]) == case["kernel_type"]
+    return sober_amd.Kernel(model, mode=case["kernel_type"])
 
 
 @pytest.mark.parametrize("pruning", [True, False])
 def test_reference_sober_next_batch_dataset_prior(ref, pruning):
     """`Sober.next_batch` on a dataset prior (SOBER/_sober.py:158-195), both dataset return shapes and the
     return_weights shape: swapped == unswapped."""
-    rng = np.random.default_rng(3)
-    pool = _t((rng.random((900, 64)) < 0.1).astype(np.float64))
-    model = _model(ref, "tanimoto", 64, 20, 77)
-    prior = ref["MG"].DatasetPrior(pool)
+    c = MG.SOBER_CASES["dataset"]
     for rw in (False, True):
-        kw = dict(n_rec=600, n_nys=40, batch_size=8, return_weights=rw, dataset_pruning=pruning,
-                  kernel_type="weighted_predictive_covariance")
-        a = _next_batch(ref, prior, model, False, 123, **dict(kw))
-        b = _next_batch(ref, prior, model, True, 123, **dict(kw))
-        assert len(a) == len(b) == 2
+        tag = f"dataset_p{int(pruning)}_w{int(rw)}"
+        kernel = _kernel(ref, c, tag)
+        call = str(ref[f"{tag}_call"])
+        assert int(ref[f"{call}_b"]) == c["batch"]
+        idx, w, _ = _replay(ref, call, kernel)
+        X_batch = _t(ref[f"{call}_X_cand"])[idx]                            # SOBER/_sober.py:181
         if rw:                                                              # (w_rchq, X_batch)
-            np.testing.assert_allclose(b[0].numpy(), a[0].numpy(), rtol=1e-9)
+            np.testing.assert_allclose(w.numpy(), ref[f"{tag}_first"], rtol=1e-9)
         else:                                                               # (idx_rchq, X_batch)
-            assert torch.equal(a[0], b[0]) and a[0].dtype == torch.int64
-        assert torch.equal(a[1], b[1])
+            if pruning:                                                     # indices into the prior's available rows
+                idx = _t(ref[f"{tag}_idx_sampled"])[idx]
+            assert idx.dtype == torch.int64 and np.array_equal(idx.numpy(), ref[f"{tag}_first"])
+        assert np.array_equal(X_batch.numpy(), ref[f"{tag}_X"])
 
 
 def test_reference_sober_next_batch_sampled_prior(ref):
     """The third return shape (X_batch alone) through `sampling_candidates` (SOBER/_sampler.py:264-323, KMeans
     Nystrom subsample for a continuous prior): swapped == unswapped."""
-    model = _model(ref, "rbf", 3, 15, 78)
-    prior = ref["MG"].UniformPrior(3)
-    kw = dict(n_rec=1500, n_nys=48, batch_size=8)
-    a = _next_batch(ref, prior, model, False, 321, **dict(kw))
-    b = _next_batch(ref, prior, model, True, 321, **dict(kw))
-    assert isinstance(a, torch.Tensor) and a.shape == (8, 3)
-    assert torch.equal(a, b)
+    c = MG.SOBER_CASES["continuous"]
+    call = str(ref["continuous_call"])
+    idx, _, _ = _replay(ref, call, _kernel(ref, c, "continuous"))
+    X_batch = _t(ref[f"{call}_X_cand"])[idx]
+    assert X_batch.shape == (8, 3) and ref["continuous_X"].shape == (8, 3)
+    assert np.array_equal(X_batch.numpy(), ref["continuous_X"])
 
 
 def test_should_reset_prior_equals_the_reference(ref):
@@ -139,27 +124,16 @@ def test_should_reset_prior_equals_the_reference(ref):
     observation histories; and `next_batch` asks for the caller's `prior_initialiser` instead of dropping
     `recycle_prior` (SOBER/_sober.py:152-155)."""
     import types
-    rng = np.random.default_rng(5)
-    RefSober = ref["_sober"].Sober
+    want = ref["reset_verdicts"]
     n_true = 0
-    for trial in range(300):
-        n_init = int(rng.integers(1, 12))
-        bs = int(rng.integers(1, 9))
-        n_batches = int(rng.integers(0, 7))
-        extra = int(rng.integers(0, bs)) if n_batches and rng.random() < 0.3 else 0
-        y = torch.from_numpy(rng.standard_normal(n_init + n_batches * bs + extra))
-        if rng.random() < 0.3:                                           # a maximum early in the history
-            y[int(rng.integers(0, n_init))] = 10.0
+    for trial, (n_init, bs, y) in enumerate(MG.reset_histories()):
         model = types.SimpleNamespace(train_targets=y)
-        for recycle in (True, False):
-            a = object.__new__(RefSober)
-            a.fbgp, a.is_bq, a.n_init, a.n_batches_until_reset = False, False, n_init, 3
-            a.pi = types.SimpleNamespace(model=model)
-            a.tensor = torch.tensor
+        for j, recycle in enumerate((True, False)):
+            ra = bool(want[trial, j])
             b = object.__new__(sober_amd.Sober)
             b.n_init, b.n_batches_until_reset, b.pi = n_init, 3, types.SimpleNamespace(model=model)
-            ra, rb = bool(a.should_reset_prior(bs, recycle)), bool(b.should_reset_prior(bs, recycle))
-            assert ra == rb, (trial, n_init, bs, n_batches, extra, recycle)
+            rb = bool(b.should_reset_prior(bs, recycle))
+            assert ra == rb, (trial, n_init, bs, len(y), recycle)
             n_true += ra
     assert 50 < n_true < 550                                             # (both verdicts occur)
 
